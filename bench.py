@@ -15,7 +15,13 @@ inputs already resident in HBM:
 Queries shard across ranks (weak scaling); the only collective is the 1 KB
 all-reduce of step 3.  Rank 0 prints ONE JSON line.
 
-python bench.py [--gpus N] [--steps K] [--warmup W]
+python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs below).  --full adds everything else the bench measures or checks — the
+roofline object with the measured copy ceiling, the CPU baselines, the parity and
+NDCG checks against the oracle and, for N > 1, the step without the gather and the
+gather's parity — to the same line.
 For N > 1 one process per GPU: either the driver launches this script under
 torch.distributed.run (WORLD_SIZE set), or — run plainly as
 `python bench.py --gpus N` — this process, before it makes any GPU call,
@@ -69,9 +75,19 @@ HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md), 6.3 TB/s measured co
 SEED = 20251212
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the roofline object (measured copy ceiling, "
+                         "committed PMC traffic), the CPU baselines, parity and NDCG@10 against "
+                         "the oracle, and for N > 1 the step without the gather and the "
+                         "gather's parity (minutes; --cpu-sample, --cpu-workers, "
+                         "--native-sample, --check and --ndcg-sample only act with it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB: the small arrays "
+                         "whole, the per-entry ones for a fixed seeded sample of queries)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--gather-topk", type=int, default=None,
@@ -109,7 +125,7 @@ def parse():
                          "at p 0.5 + the 2,681,468-id NQ pool, Gamma / Beta / ln-Beta scores, the "
                          "real NQ test qrels planted at Geometric(0.15) ranks); legacy = rounds "
                          "1-4's exp-decay generator (qf_synth_runs)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     a.wl = WORKLOADS[a.workload]
     if a.qpp_index is None:
         a.qpp_index = a.wl["qpp_index"]
@@ -576,6 +592,23 @@ def ndcg_delta_learned(p: Pipeline, dev_vals, nq: int):
             abs(float(np.nanmean(dv)) - float(np.nanmean(ref))))
 
 
+def ndcg_delta_vs_ref(p: Pipeline, dev_vals, nq: int):
+    """The result line's ndcg10_delta_vs_ref for the workload's methods (None: no CPU
+    reference path for them)."""
+    if all(m in METHODS for m in p.methods):
+        dq, dm = ndcg_delta(p, dev_vals, nq)
+        ref = ("CPU reference path: C oracle fusion + trec_eval restatement "
+               "(oracle/), scores as the .res text")
+    elif p.methods == ["learned"]:
+        dq, dm = ndcg_delta_learned(p, dev_vals, nq)
+        ref = ("CPU reference path: QPP by the Java restatement (oracle/qpp_oracle.c), "
+               "min-max + '%.6f', LightGBM walk restated (oracle/lgbm_oracle.py), "
+               "pandas' Kahan groupby-sum in run order, trec_eval restatement")
+    else:
+        return None
+    return {"queries": nq, "max_abs_per_query": dq, "max_abs_mean": dm, "ref": ref}
+
+
 def host_sample(p: Pipeline, nq: int):
     """Copy the first nq queries' inputs + device outputs to host numpy.  When the
     step's fusion took its W-* weights from the QPP predictors (qf_fuse_qpp), `w` is
@@ -805,6 +838,20 @@ def timed_loop(p: Pipeline, steps: int, world: int, dev) -> float:
     return elapsed
 
 
+def ramp_clocks(dev, nbytes: int = 1 << 30, copies: int = 88):
+    """The plain run's clock ramp: ~30 ms of HBM traffic (qf_stream_copy, untimed, one
+    synchronize at its end) before the warmup steps, the traffic copy_ceiling_gbs puts
+    there in a --full run, so that both time the same step ("Clock ramp")."""
+    from qppfuse import _lib
+    a = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    b = torch.empty_like(a)
+    a.fill_(1.0)
+    s = torch.cuda.current_stream().cuda_stream
+    for _ in range(copies):
+        _lib.call("qf_stream_copy", b.data_ptr(), a.data_ptr(), nbytes, s)
+    torch.cuda.synchronize()
+
+
 def copy_ceiling_gbs(dev, nbytes: int = 1 << 30, reps: int = 40) -> dict:
     """Measured device-to-device copy rates (read + write bytes / s): the practical HBM
     ceiling next to the 8 TB/s spec peak.  `kernel`: the library's
@@ -835,13 +882,77 @@ def copy_ceiling_gbs(dev, nbytes: int = 1 << 30, reps: int = 40) -> dict:
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_QUERIES = 64
+
+
+def dump_outputs(p: Pipeline, out_dir) -> dict:
+    """Write what the last step left in the step's output buffers — what a caller of the
+    path receives — as out_dir/<name>.npy (float32 / float64, DUMP_LIMIT_BYTES at most).
+    Whole: union_count [Q]; with QPP the raw predictors qpp_raw [Q*R, 13], their column
+    extremes qpp_colminmax [2*R*13] and the .qpp table qpp_micro [Q*R, 13] (not C5: its
+    step normalises on the fly); fusion_weights [Q, R] where the step made them (C4, C5).
+    Per entry, for a fixed sample of queries (sample_queries: DUMP_SAMPLE_QUERIES ids
+    drawn without replacement from default_rng(SEED), ascending; every query when the
+    shard has no more), one row per sampled query, padded to the longest with -1 (ids)
+    or 0 (values): sample_norm_micro [S, n] the .norm.res micro-units in list order;
+    sample_union_docid [S, n] and sample_fused [S, M, n] in first-seen order and
+    sample_perm [S, M, n], the first-seen index of rank i, each to the query's
+    union_count (what lies beyond it in the device buffers is never written).
+    The integers are exact in the float types chosen (micro-units and perm < 2^24 in
+    float32; ids and counts in float64).  Returns {name: shape}."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    Q, R, o = p.Q, p.R, p.out
+    M = len(p.methods)
+    arrays = {"union_count": o.union_count[:Q].cpu().numpy().astype(np.float64)}
+    if p.args.wl["qpp"]:
+        arrays["qpp_raw"] = p.qraw.cpu().numpy()
+        arrays["qpp_colminmax"] = p.mm.cpu().numpy()
+        if "learned" not in p.methods:
+            arrays["qpp_micro"] = p.qmicro.cpu().numpy().reshape(Q * R, 13).astype(np.float64)
+    if p.w is not None:
+        arrays["fusion_weights"] = p.w.cpu().numpy().astype(np.float64).reshape(Q, R)
+    off = p.off.cpu().numpy()
+    uc = o.union_count[:Q].cpu().numpy().astype(np.int64)
+    # the sample's size from the budget the whole arrays leave (fewer queries when the
+    # lists are long), by the shard's longest query so that it is the same for any sample
+    per_query = int((off[R::R] - off[:-R:R]).max()) * (4 + 8 + M * (8 + 4)) + 8
+    room = DUMP_LIMIT_BYTES - 4096 - sum(a.nbytes for a in arrays.values())  # .npy headers
+    S = max(1, min(Q, DUMP_SAMPLE_QUERIES, room // per_query))
+    sample = np.sort(np.random.default_rng(SEED).choice(Q, S, replace=False))
+    n = int((off[(sample + 1) * R] - off[sample * R]).max())
+    micro = np.zeros((S, n), np.float32)
+    udoc = np.full((S, n), -1.0, np.float64)
+    fused = np.zeros((S, M, n), np.float64)
+    perm = np.full((S, M, n), -1.0, np.float32)
+    for i, q in enumerate(sample):
+        b, e, u = int(off[q * R]), int(off[(q + 1) * R]), int(uc[q])
+        micro[i, :e - b] = p.micro[b:e].cpu().numpy()
+        udoc[i, :u] = o.union_docid[b:b + u].cpu().numpy().view(np.uint32)
+        fused[i, :, :u] = o.fused[:, b:b + u].cpu().numpy()
+        pm = o.perm[:, b:b + u].cpu().numpy()
+        perm[i, :, :u] = pm.view(np.uint32 if o.wide else np.uint16)
+    arrays.update(sample_queries=(p.q_begin + sample).astype(np.float64),
+                  sample_norm_micro=micro, sample_union_docid=udoc, sample_fused=fused,
+                  sample_perm=perm)
+    total = 4096 + sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes "
+                         f"(limit {DUMP_LIMIT_BYTES}): fewer --queries or a smaller --k")
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def progress(msg: str):
     """One line on stderr per phase (long runs are not silent; stdout stays one JSON line)."""
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    args = parse(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
     # stdout carries exactly one JSON line: everything else (library banners such as
@@ -849,6 +960,15 @@ def main():
     out_fd = os.dup(1)
     sys.stdout.flush()
     os.dup2(2, 1)
+    try:
+        return run(args, out_fd)
+    finally:  # a caller in this process (a test) gets its stdout back
+        sys.stdout.flush()
+        os.dup2(out_fd, 1)
+        os.close(out_fd)
+
+
+def run(args, out_fd):
     world, rank, dev = setup_dist(args)
     if args.gather_topk is None:
         args.gather_topk = 100 if world > 1 else 0
@@ -859,15 +979,19 @@ def main():
     progress(f"rank {rank}: {p.Q} queries x {p.R} x top-{p.K} resident; warmup {args.warmup}")
     # the device-copy ceiling of the roofline object, measured before the warmup steps:
     # ~10 ms of HBM traffic that also takes the GPU out of its idle clocks, so a short
-    # timed region (the driver's 5 + 20 steps) sees the steady-state step time
-    copy = copy_ceiling_gbs(dev)
-    copy_gbs = copy["kernel"]
+    # timed region (the driver's 5 + 20 steps) sees the steady-state step time.  A plain
+    # run has the traffic for that reason alone (ramp_clocks)
+    copy = copy_ceiling_gbs(dev) if args.full else ramp_clocks(dev)
     for _ in range(args.warmup):
         p.step()
     p.drain()
     p.wait_s, p.timed_steps = 0.0, 0
     progress(f"rank {rank}: timing {args.steps} steps")
     elapsed = timed_loop(p, args.steps, world, dev)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # rank 0's shard, as the last timed step left it
+        dumped = dump_outputs(p, args.dump_outputs)
+        progress(f"wrote {len(dumped)} arrays to {args.dump_outputs}")
     total_q = p.Q * args.steps
     if world > 1:
         import torch.distributed as dist
@@ -875,7 +999,7 @@ def main():
         dist.all_reduce(qt)
         total_q = int(qt.item()) * args.steps
     without_gather = None
-    if world > 1 and args.gather_topk > 0:  # the same step without the collective
+    if args.full and world > 1 and args.gather_topk > 0:  # the same step without the collective
         k, args.gather_topk = args.gather_topk, 0
         ms_fuse = list(p.ev)
         e2 = timed_loop(p, args.steps, world, dev)
@@ -899,22 +1023,24 @@ def main():
                     "block), so the host wait is ~0 there; the gather's cost on the step is "
                     "ms_per_step - step_ms_without_gather (DESIGN.md §7's ingress budget)"}
     value = total_q / elapsed
-    fuse_ms = p.fuse_kernel_ms()
     fbytes, mean_u = p.fuse_bytes()
-    achieved = fbytes / (fuse_ms * 1e-3) / 1e9
-    traffic, traffic_src = pmc_traffic(args)
-    valu = pmc_valu(args)
-    progress(f"rank {rank}: {elapsed / args.steps * 1e3:.3f} ms/step; parity + NDCG checks")
-    parity = check_parity(p, min(args.check, p.Q)) if args.check > 0 else None
-    gparity = p.gather_parity()
-    ndcg_vals, eval_ms = ndcg_device(p)
+    progress(f"rank {rank}: {elapsed / args.steps * 1e3:.3f} ms/step")
+    if args.full:
+        fuse_ms = p.fuse_kernel_ms()
+        achieved = fbytes / (fuse_ms * 1e-3) / 1e9
+        traffic, traffic_src = pmc_traffic(args)
+        valu = pmc_valu(args)
+        progress(f"rank {rank}: parity + NDCG checks")
+        parity = check_parity(p, min(args.check, p.Q)) if args.check > 0 else None
+        gparity = p.gather_parity()
+        ndcg_vals, eval_ms = ndcg_device(p)
     result = None
     if rank == 0:
         cpu = None
         ported = all(m in METHODS or m == "learned" for m in p.methods)
         per_worker = (CPU_SAMPLE_PER_WORKER[args.workload] if args.cpu_sample is None
                       else args.cpu_sample)
-        if world == 1 and per_worker > 0 and ported:
+        if args.full and world == 1 and per_worker > 0 and ported:
             workers = args.cpu_workers or min(16, os.cpu_count() or 1)
             progress(f"CPU baseline: {workers} processes x {per_worker} queries")
             c = cpu_baseline_port(p, per_worker, workers)
@@ -968,44 +1094,40 @@ def main():
                        "qids": (None if p.qids is None else
                                 f"real BEIR test qids, namespaced: {p.qids[0]} .. {p.qids[-1]}"),
                        "without_gather": without_gather, "gather": gather_info},
-            "roofline": {"bound": "hbm", "kernel": "qf_fuse", "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": fbytes,
-                         "kernel_ms": round(fuse_ms, 4),
-                         # the roof it actually meets: VALU issue
-                         "valu_issue_frac": None if valu is None else round(
-                             valu / N_SIMDS / (fuse_ms * 1e6) / VALU_PEAK_PER_SIMD_NS, 4),
-                         "valu_insts_per_launch": valu,
-                         "copy_ceiling_gbs": round(copy_gbs, 1),
-                         "copy_ceiling_source": "qf_stream_copy: 16 B/lane non-temporal "
-                                                "copy, one access per thread, one-shot grid, "
-                                                "1 GiB, read + write, best of 4 x 10",
-                         "copy_blit_gbs": round(copy["blit"], 1),
-                         "frac_of_copy_ceiling": round(achieved / copy_gbs, 4)},
-            "cpu_baseline": cpu,
-            "parity_vs_oracle": {"queries": min(args.check, p.Q), "bit_exact": parity},
-            "gather_parity": gparity,
-            "ndcg10": {m: round(float(np.nanmean(ndcg_vals[i])), 6)
-                       for i, m in enumerate(p.methods)},
-            "ndcg10_eval_ms": round(eval_ms, 4),
+            "full": args.full,
         }
-        if world == 1 and args.ndcg_sample > 0 and all(m in METHODS for m in p.methods):
-            nq = min(args.ndcg_sample, p.Q)
-            dq, dm = ndcg_delta(p, ndcg_vals, nq)
-            result["ndcg10_delta_vs_ref"] = {
-                "queries": nq, "max_abs_per_query": dq, "max_abs_mean": dm,
-                "ref": "CPU reference path: C oracle fusion + trec_eval restatement "
-                       "(oracle/), scores as the .res text"}
-        elif world == 1 and args.ndcg_sample > 0 and p.methods == ["learned"]:
-            nq = min(args.ndcg_sample, p.Q)
-            dq, dm = ndcg_delta_learned(p, ndcg_vals, nq)
-            result["ndcg10_delta_vs_ref"] = {
-                "queries": nq, "max_abs_per_query": dq, "max_abs_mean": dm,
-                "ref": "CPU reference path: QPP by the Java restatement (oracle/qpp_oracle.c), "
-                       "min-max + '%.6f', LightGBM walk restated (oracle/lgbm_oracle.py), "
-                       "pandas' Kahan groupby-sum in run order, trec_eval restatement"}
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": str(args.dump_outputs), "arrays": dumped}
+        if args.full:
+            copy_gbs = copy["kernel"]
+            result.update({
+                "roofline": {"bound": "hbm", "kernel": "qf_fuse", "achieved": round(achieved, 2),
+                             "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 4),
+                             "traffic": traffic, "traffic_source": traffic_src,
+                             "algorithmic_bytes_per_launch": fbytes,
+                             "kernel_ms": round(fuse_ms, 4),
+                             # the roof it actually meets: VALU issue
+                             "valu_issue_frac": None if valu is None else round(
+                                 valu / N_SIMDS / (fuse_ms * 1e6) / VALU_PEAK_PER_SIMD_NS, 4),
+                             "valu_insts_per_launch": valu,
+                             "copy_ceiling_gbs": round(copy_gbs, 1),
+                             "copy_ceiling_source": "qf_stream_copy: 16 B/lane non-temporal "
+                                                    "copy, one access per thread, one-shot "
+                                                    "grid, 1 GiB, read + write, best of 4 x 10",
+                             "copy_blit_gbs": round(copy["blit"], 1),
+                             "frac_of_copy_ceiling": round(achieved / copy_gbs, 4)},
+                "cpu_baseline": cpu,
+                "parity_vs_oracle": {"queries": min(args.check, p.Q), "bit_exact": parity},
+                "gather_parity": gparity,
+                "ndcg10": {m: round(float(np.nanmean(ndcg_vals[i])), 6)
+                           for i, m in enumerate(p.methods)},
+                "ndcg10_eval_ms": round(eval_ms, 4),
+            })
+            if world == 1 and args.ndcg_sample > 0:
+                delta = ndcg_delta_vs_ref(p, ndcg_vals, min(args.ndcg_sample, p.Q))
+                if delta is not None:
+                    result["ndcg10_delta_vs_ref"] = delta
         os.write(out_fd, (json.dumps(result) + "\n").encode())
     if world > 1:
         dist.destroy_process_group()

@@ -29,11 +29,11 @@ for i in $(seq ${REPS:-3}); do
         python3 tools/ab_summary.py pmc "$OUT/$n" "$OUT/$n.log" ;;
       kbench)
         QPPFUSE_LIB=$L timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv \
-          -d "$OUT/$n" -o run -- python3 bench.py --warmup 2 --steps 10 --cpu-sample 0 \
+          -d "$OUT/$n" -o run -- python3 bench.py --full --warmup 2 --steps 10 --cpu-sample 0 \
           --native-sample 0 --check 0 --ndcg-sample 0 $BENCH_ARGS > "$OUT/$n.log" 2>&1 || { tail -20 "$OUT/$n.log"; exit 1; }
         python3 tools/ab_summary.py kbench "$OUT/$n" "$OUT/$n.log" ;;
       bench)
-        QPPFUSE_LIB=$L timeout -k 10 300 python3 -u bench.py --warmup 5 --steps 20 --cpu-sample 0 \
+        QPPFUSE_LIB=$L timeout -k 10 300 python3 -u bench.py --full --warmup 5 --steps 20 --cpu-sample 0 \
           --native-sample 0 $BENCH_ARGS > "$OUT/$n.json" 2> "$OUT/$n.err" || { tail -20 "$OUT/$n.err"; exit 1; }
         python3 tools/ab_summary.py bench "$OUT/$n.json" ;;
       *) echo "unknown mode $MODE"; exit 2 ;;

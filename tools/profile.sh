@@ -5,7 +5,7 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 OUT=${1:-gpurun_out/prof}
-ARGS="--steps 10 --warmup 2 --cpu-sample 0 --native-sample 0 --check 0"
+ARGS="--full --steps 10 --warmup 2 --cpu-sample 0 --native-sample 0 --check 0"
 mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py $ARGS > $OUT/bench_trace.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o run -- python3 bench.py $ARGS > $OUT/bench_fetch.log 2>&1
